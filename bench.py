@@ -22,7 +22,9 @@ side stream. --simulate-world W replays the exchange of W ranks on one GPU (para
 --sim-wire adds the modelled xGMI transfer time as CU-holding busy kernels.
 
 Usage:
-  python bench.py                                   # 1 GPU
+  python bench.py                                   # 1 GPU: set up, warm up, time --steps steps
+  python bench.py --full                            # + per-bucket timings and the top-1 run
+  python bench.py --dump-outputs DIR                # + the last timed step's outputs as .npy
   torchrun --nproc-per-node 8 bench.py --gpus 8     # one node
 Prints ONE JSON line on rank 0.
 """
@@ -40,13 +42,19 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 def _miopen_cache_env() -> None:
     """Point MIOpen's find-db and compiled-kernel cache at an in-repo directory (unless the user
     already chose one): the solver search and kernel compilation of a fresh box then run once per
-    image, not once per run (a cold find for ResNet-50 takes minutes)."""
+    image, not once per run (a cold find for ResNet-50 takes minutes). A checkout this user
+    cannot write to (built by someone else, mounted read-only) keeps MIOpen's own per-user
+    locations instead."""
     base = os.path.join(ROOT, ".miopen")
     for var, sub in (("MIOPEN_USER_DB_PATH", "db"), ("MIOPEN_CUSTOM_CACHE_DIR", "cache")):
         if var not in os.environ:
             path = os.path.join(base, sub)
-            os.makedirs(path, exist_ok=True)
-            os.environ[var] = path
+            try:
+                os.makedirs(path, exist_ok=True)
+            except OSError:
+                continue
+            if os.access(path, os.W_OK | os.X_OK):
+                os.environ[var] = path
 
 
 _miopen_cache_env()
@@ -85,10 +93,19 @@ def parse():
     ap.add_argument("--no-fused", action="store_true", help="disable fused HIP nn kernels")
     ap.add_argument("--json-out", default="")
     ap.add_argument("--pool", type=int, default=4, help="distinct synthetic batches cycled")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed run also measure what the headline figure does not "
+                         "need: one extra step with per-bucket compress / exchange / decode "
+                         "timings (comm.bucket_us) and the accuracy half of the metric "
+                         "(--acc-steps). A plain run reports both as not measured")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as "
+                         "DIR/<name>.npy (float32): loss, logits, and a fixed seeded sample of "
+                         "the updated parameters")
     ap.add_argument("--acc-steps", type=int, default=1000,
-                    help="after the timed run: train a fresh ResNet-50 with the same compression "
-                         "this many steps at 128 px and report its held-out top-1 "
-                         "(train/accuracy.py); 0 = not measured")
+                    help="with --full, after the timed run: train a fresh ResNet-50 with the "
+                         "same compression this many steps at 128 px and report its held-out "
+                         "top-1 (train/accuracy.py); 0 = not measured")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend (nccl = RCCL on ROCm)")
     ap.add_argument("--share-gpu", action="store_true",
@@ -186,6 +203,31 @@ def _reference_points(steps: int) -> str:
             " (layer_wise_aaai20_amd/train/accuracy_reference.json)")
 
 
+DUMP_PARAM_SAMPLE = 1 << 22       # parameters kept by --dump-outputs (16 MiB of float32)
+
+
+def dump_outputs(tr, loss, path: str) -> None:
+    """--dump-outputs: what the last timed step handed its caller (the loss, and the logits the
+    trainer keeps for ``last_top1``) and what it left behind (the updated parameters, in
+    ``module.parameters()`` order and logical NCHW element order; a fixed seeded sample of
+    ``DUMP_PARAM_SAMPLE`` of them, sorted by position)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = tr._last[0]
+    flat = torch.cat([p.detach().reshape(-1).float() for p in tr.ddp.module.parameters()])
+    n = flat.numel()
+    if n > DUMP_PARAM_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(2020))
+        idx = idx[:DUMP_PARAM_SAMPLE].sort().values
+    else:
+        idx = torch.arange(n)
+    arrays = {"loss": loss.detach().float().reshape(1),
+              "logits": out.detach().float(),
+              "params_sample": flat[idx.to(flat.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def simulate(args) -> None:
     """--simulate-world W (train/simworld.py): JSON lines, no benchmark line."""
     from layer_wise_aaai20_amd.train.simworld import simulate_imagenet
@@ -239,6 +281,9 @@ def main():
 
     from layer_wise_aaai20_amd.train.imagenet import build_trainer
 
+    # the same initial weights (and stochastic-codec draws) in every run with the same arguments:
+    # with the seeded batches below, two runs start from identical inputs (--dump-outputs)
+    torch.manual_seed(2020)
     tr = build_trainer(model=args.model, device=dev, compress=args.compress, method=args.method,
                        K=args.ratio, V=args.threshold, qstates=args.qstates,
                        error_feedback=args.ef, bucket_cap_mb=args.bucket_mb, dtype=args.dtype,
@@ -251,6 +296,7 @@ def main():
                        # no graph-vs-eager timing decision: it would spill syncs into the timed
                        # steps (the captured ResNet-50 step is the faster one: 24.3 vs 27.2 ms)
                        graph_auto=False)
+    torch.manual_seed(2020 + rank)        # (draws after the shared initialisation: per rank)
     B, S = args.batch, args.image_size
     g = torch.Generator(device=dev)
     g.manual_seed(1234 + rank)
@@ -276,8 +322,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    loss = None
     for i in range(args.steps):
-        tr.step(*pool[(args.warmup + i) % len(pool)])
+        loss = tr.step(*pool[(args.warmup + i) % len(pool)])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -287,19 +334,24 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    ms = dt / args.steps * 1e3
+    ms = dt / max(args.steps, 1) * 1e3
     graphed = tr.graph_replays >= args.steps
-    # ---- outside the timed region: per-bucket compress / exchange / decode µs of one step,
-    # then the accuracy half of the metric (a short training run of the same configuration)
+    if args.dump_outputs and rank == 0 and loss is not None:
+        dump_outputs(tr, loss, args.dump_outputs)
     eng = tr.ddp.engine
-    eng.timing = True
-    tr.step(*pool[0])
-    bucket_us = eng.read_timings()
-    eng.timing = False
+    # ---- --full, outside the timed region: per-bucket compress / exchange / decode µs of one
+    # more step, then the accuracy half of the metric (a short training run of the same
+    # configuration)
+    bucket_us = None
+    if args.full:
+        eng.timing = True
+        tr.step(*pool[0])
+        bucket_us = eng.read_timings()
+        eng.timing = False
     stats = tr.ddp.sync_stats()
     overflow = eng.read_overflow()
     acc = None
-    if args.acc_steps > 0:
+    if args.full and args.acc_steps > 0:
         del tr                            # (free the 224 px trainer's graph pool first)
         torch.cuda.empty_cache()
         from layer_wise_aaai20_amd.train.accuracy import short_run_top1
@@ -344,12 +396,14 @@ def main():
                       f"gfx950 tuning table) on the class-conditional synthetic task; "
                       f"chance 0.1%; top-5 {acc['top5']}%; train loss {acc['loss_first20']} -> "
                       f"{acc['loss_last20']} (train/accuracy.py)" + _reference_points(acc['steps'])
-                      if acc else "not measured (--acc-steps 0)"),
+                      if acc else "not measured (measured with --full and --acc-steps > 0)"),
         "hip_graph": graphed,
         "comm": {"backend": dist.get_backend() if world > 1 else "none (1 rank)",
                  "world_size": dist.get_world_size() if world > 1 else 1,
-                 "bucket_us": [{k: (round(v, 1) if isinstance(v, float) else v)
-                                for k, v in b.items()} for b in bucket_us]},
+                 # (None: not measured, a plain run takes no extra step for it; --full does)
+                 "bucket_us": None if bucket_us is None else [
+                     {k: (round(v, 1) if isinstance(v, float) else v) for k, v in b.items()}
+                     for b in bucket_us]},
         "config": {
             "model": args.model,
             "global_batch": world * B,

@@ -7,6 +7,7 @@ mkdir -p gpurun_out
 : > gpurun_out/matrix.jsonl
 b() {  # name args...
   local name=$1; shift
+  set -- --full "$@"   # the matrix records each method's top-1 as well as its speed
   echo "=== $name: $*"
   timeout -k 10 400 python bench.py --steps 15 --warmup 6 "$@" > "gpurun_out/m_$name.log" 2>&1
   local rc=$?

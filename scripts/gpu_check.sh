@@ -19,7 +19,7 @@ run() {  # name timeout cmd...
 run build 600 python -m layer_wise_aaai20_amd.csrc.build
 run pytest_gpu 900 python -m pytest tests -m gpu -x -q
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-run bench 600 python bench.py --steps $STEPS --warmup 8
+run bench 600 python bench.py --steps $STEPS --warmup 8 --full
 if [ "${PROFILE:-1}" = "1" ]; then
   run rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o bench --output-format csv -- python bench.py --steps 5 --warmup 3
 fi

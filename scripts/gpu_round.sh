@@ -19,10 +19,10 @@ for step in ${STEPS_TO_RUN:-pytest smoke bench share2}; do
   case $step in
     pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 8 ;;
+    bench) run bench 600 python bench.py --steps 20 --warmup 8 --full ;;
     share2) run share2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
               --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 4 --warmup 2 \
-              --batch 64 --share-gpu --backend gloo ;;
+              --batch 64 --share-gpu --backend gloo --full ;;
     savedb) tar -C . -czf gpurun_out/miopen_cache.tgz .miopen && ls -la gpurun_out/miopen_cache.tgz ;;
     prof) run prof 900 bash scripts/prof_step.sh ${PROF_TAG:-step} ;;
   esac

@@ -6,6 +6,6 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 unset LWAAAI_TUNE_FILE
-STEPS="bench1:420:python -u bench.py;;bench2:420:python -u bench.py;;\
+STEPS="bench1:420:python -u bench.py --full;;bench2:420:python -u bench.py --full;;\
 mgpu:600:LWAAAI_TEST_SHARE_GPU=1 python -u -m pytest tests/test_multigpu_gpu.py -x -v \
 --timeout 280 --timeout-method thread" bash scripts/gpu_steps.sh

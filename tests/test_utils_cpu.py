@@ -177,7 +177,9 @@ def test_env_local_rank(monkeypatch):
     assert comm.env_local_rank() == 3
     monkeypatch.setenv("LOCAL_RANK", "2")
     assert comm.env_local_rank() == 2
-    assert comm.bind_rank_device(5).type == "cpu"        # no GPU in this container
+    # without a visible GPU a rank lands on the CPU (patched: the suite also runs on GPU hosts)
+    monkeypatch.setattr(comm.torch.cuda, "is_available", lambda: False)
+    assert comm.bind_rank_device(5).type == "cpu"
 
 
 def test_ddp_rejects_single_process_multi_gpu():
